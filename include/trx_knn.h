@@ -204,6 +204,61 @@ int trx_index_last_stats(const trx_index* idx, trx_search_stats* out);
  * it before handing trx_index_last_stats a buffer (the struct grew in 0.2: `late_fallback`, `n_rescored`, `n_rescanned`). */
 int trx_search_stats_size(void);
 
+/* ---- range search: every row within a radius ----------------------------------------------------------------------------
+ * lims, D, I = index.range_search(x, radius): faiss::IndexFlat::range_search (IndexFlatL2 / IndexFlatIP) and the
+ * RangeSearchResult it fills.  The reference does not call it (retrieve_faiss.py:65-71 asks for k neighbours only); it is the other
+ * query method of every faiss.Index, and what a radius question of the corpus asks: every train reaction within Hamming distance r of
+ * a test reaction (L2 on the 0/1 Morgan vectors of retrieve_faiss.py:36-44), every near-duplicate of a test row.
+ *
+ * Semantics.  Query i's results are D[lims[i] .. lims[i+1]) and I[lims[i] .. lims[i+1]), lims int64 [nq + 1], lims[0] = 0.
+ *   L2: D is the SQUARED distance, as in trx_index_search, and a row is returned iff D < radius (strict);
+ *   IP: a row is returned iff D > radius (strict).
+ *   D = (float) of the canonical fp64 score (the fma chain of "Results" above: the value trx_index_search reports for the same pair)
+ *   and membership is decided on that D, so every returned value satisfies the predicate the caller checks.  This is the canonical
+ *   rule, not FAISS' fp32 sgemm: a row whose score lies within rounding of the radius may be in one answer and not in the other.
+ *   Within a query rows come in ASCENDING ID (CPU FAISS' flat index appends in scan order, the same order); the output does not
+ *   depend on batches or corpus splits.  A NaN score never satisfies the predicate; +-inf scores compare as values; hostile rows and
+ *   queries (NaN, +-inf, float32 overflow) score exactly as in a search.  An empty index, nq == 0, or a radius no row meets give
+ *   lims of zeros and no results.  radius is a float; a NaN radius is refused (TRX_EINVAL): no row can satisfy it, and FAISS' answer
+ *   to it is not defined either.
+ * How.  A fixed-threshold scan: a query's threshold is the key bound of its predicate lowered by twice its key error bound (DESIGN.md
+ * section 11), every row above it is listed (at most 4 x 8 x 127 = 4,064 per query), re-scored exactly and filtered, and the
+ * survivors sorted by id.  A query whose lists overflow (more listed rows than that) takes the exact fp64 scan of the whole index,
+ * correct for any result size at 0.17 ms per query at 1,000,000 x 768 rows.  Queries run in blocks of 65,536; the answer is held by
+ * the index, in device memory, until the next range search, trx_index_reset or trx_index_destroy: memory grows with the answer, not
+ * with nq x n.  Synchronous: on return lims is final. */
+
+/* HOST in: q as for trx_index_search (any TRX_DTYPE_*), lims int64[nq + 1] in host memory, caller-allocated.  The results stay in
+ * the index until trx_index_range_fetch. */
+int trx_index_range_search(trx_index* idx, const void* q, int64_t nq, int dtype, float radius, int64_t* lims);
+
+/* Copy the answer of the last range search out: D float[lims[nq]], I int64[lims[nq]] in host memory (null when lims[nq] == 0). */
+int trx_index_range_fetch(trx_index* idx, float* D, int64_t* I);
+
+/* Same with q (TRX_DTYPE_F32 / _BF16) and lims in DEVICE memory of the index's device; runs on `stream` and returns when lims is final
+ * (the caller reads lims[nq] to size D and I). */
+int trx_index_range_search_device(trx_index* idx, const void* q, int64_t nq, int dtype, float radius, int64_t* lims, void* stream);
+
+/* Same as trx_index_range_fetch into DEVICE memory, on `stream` (stream-ordered: D and I are final when the stream is). */
+int trx_index_range_fetch_device(trx_index* idx, float* D, int64_t* I, void* stream);
+
+/* Counters of the most recent range search (its own struct: trx_search_stats stays as it is). */
+typedef struct trx_range_stats {
+    int64_t nq;            /* queries in the call */
+    int64_t n_results;     /* lims[nq] */
+    int64_t n_exact;       /* queries that took the exact fp64 scan of the whole index (lists overflowed, hostile query, or an
+                              index with more hostile rows than it folds in) */
+    int32_t n_splits;      /* corpus splits of the fixed-threshold scan (at most 4) */
+    int32_t scan_launches; /* fixed-threshold scan launches (one per block of 65,536 queries) */
+    float scan_ms;         /* HIP-event time of the scan kernel(s), valid when timing is enabled */
+    float total_ms;        /* HIP-event time of the whole call, ditto */
+    int32_t int8_scan;     /* the form the scan ran in, as trx_search_stats.int8_scan */
+    int32_t reserved;
+} trx_range_stats;
+
+int trx_index_last_range_stats(const trx_index* idx, trx_range_stats* out);
+int trx_range_stats_size(void);
+
 /* Enable (1) / disable (0) HIP-event timing of the scan kernel inside search calls.  Timing makes
  * begin synchronise after every batch; leave it off for overlapped pipelines. */
 int trx_index_set_timing(trx_index* idx, int enabled);

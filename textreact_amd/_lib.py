@@ -23,6 +23,8 @@ SYMBOLS = [
     "trx_index_set_timing", "trx_last_error", "trx_version",
     "trx_merge_topk_device_s64", "trx_index_set_tie_rule", "trx_faiss_tie_order_device",
     "trx_host_convert", "trx_host_threads",
+    "trx_index_range_search", "trx_index_range_fetch", "trx_index_range_search_device", "trx_index_range_fetch_device",
+    "trx_index_last_range_stats", "trx_range_stats_size",
 ]
 
 
@@ -31,6 +33,12 @@ class SearchStats(ctypes.Structure):
                 ("n_splits", ctypes.c_int32), ("exact_class", ctypes.c_int32), ("scan_launches", ctypes.c_int32),
                 ("scan_ms", ctypes.c_float), ("total_ms", ctypes.c_float), ("late_fallback", ctypes.c_int32),
                 ("n_rescored", ctypes.c_int32), ("n_rescanned", ctypes.c_int32), ("int8_scan", ctypes.c_int32)]
+
+
+class RangeStats(ctypes.Structure):
+    _fields_ = [("nq", ctypes.c_int64), ("n_results", ctypes.c_int64), ("n_exact", ctypes.c_int64), ("n_splits", ctypes.c_int32),
+                ("scan_launches", ctypes.c_int32), ("scan_ms", ctypes.c_float), ("total_ms", ctypes.c_float), ("int8_scan", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
 
 
 class TrxError(RuntimeError):
@@ -87,11 +95,20 @@ def lib():
     L.trx_host_convert.argtypes = [vp, i32, i64, vp, i32]
     L.trx_index_last_stats.argtypes = [vp, ctypes.POINTER(SearchStats)]
     L.trx_index_set_timing.argtypes = [vp, i32]
+    f32 = ctypes.c_float
+    L.trx_index_range_search.argtypes = [vp, vp, i64, i32, f32, vp]
+    L.trx_index_range_fetch.argtypes = [vp, vp, vp]
+    L.trx_index_range_search_device.argtypes = [vp, vp, i64, i32, f32, vp, vp]
+    L.trx_index_range_fetch_device.argtypes = [vp, vp, vp, vp]
+    L.trx_index_last_range_stats.argtypes = [vp, ctypes.POINTER(RangeStats)]
     L.trx_last_error.restype = ctypes.c_char_p
     L.trx_version.restype = ctypes.c_char_p
     if L.trx_search_stats_size() != ctypes.sizeof(SearchStats):
         raise TrxError("libtrxknn.so was built with another trx_search_stats (%d bytes, this binding has %d): rebuild it"
                        % (L.trx_search_stats_size(), ctypes.sizeof(SearchStats)))
+    if L.trx_range_stats_size() != ctypes.sizeof(RangeStats):
+        raise TrxError("libtrxknn.so was built with another trx_range_stats (%d bytes, this binding has %d): rebuild it"
+                       % (L.trx_range_stats_size(), ctypes.sizeof(RangeStats)))
     _lib = L
     return L
 

@@ -5,6 +5,7 @@
 #include "../../include/trx_knn.h"
 #include "knn_common.h"
 #include "knn_host.h"
+#include "knn_range.h"
 
 #include <algorithm>
 #include <mutex>
@@ -124,6 +125,12 @@ struct trx_index {
     DevBuf w_tie;             // TRX_TIES_FAISS: the canonical top 2k (D, I, S) the FAISS order is derived from
     int tie_rule = TRX_TIES_BY_ID;
     trx_search_stats stats{};
+    // the range search's answer (trx_index_range_fetch copies it out): one device chunk per query batch, in query order
+    struct RangeChunk { float* D; int64_t* I; int64_t count; };
+    std::vector<RangeChunk> rng_chunks;
+    int64_t rng_total = 0;
+    DevBuf w_rng, w_rlims;    // its per-batch workspace (counts, exact-path list, seeds), the host entry's device lims
+    trx_range_stats rstats{};
     bool timing = false;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     hipStream_t copy_stream = nullptr;      // host entry points: the next block's host-to-device copy under this block's search
@@ -146,6 +153,13 @@ struct trx_index {
 };
 
 static int set_device(const trx_index* idx) { HIPCHK(hipSetDevice(idx->device)); return TRX_OK; }
+
+// drop the answer of the last range search (the caller has set the device)
+static void range_release(trx_index* idx) {
+    for (auto& c : idx->rng_chunks) { if (c.D) (void)hipFree(c.D); if (c.I) (void)hipFree(c.I); }
+    idx->rng_chunks.clear();
+    idx->rng_total = 0;
+}
 
 static int read_stats(trx_index* idx, hipStream_t st, HostStats* out) {
     HIPCHK(hipMemcpyAsync(out, idx->w_stats.p, sizeof(HostStats), hipMemcpyDeviceToHost, st));
@@ -231,8 +245,9 @@ void trx_index_destroy(trx_index* idx) {
     if (idx->cbias8) (void)hipFree(idx->cbias8);
     if (idx->C4) (void)hipFree(idx->C4);
     DevBuf* bufs[] = {&idx->w_stamp, &idx->w_stats, &idx->w_qnorm2, &idx->w_flag, &idx->w_exact, &idx->w_io, &idx->w_tmp, &idx->w_cls, &idx->w_tie,
-                      &idx->w_stage[0], &idx->w_stage[1], &idx->w_wide, &idx->w_special};
+                      &idx->w_stage[0], &idx->w_stage[1], &idx->w_wide, &idx->w_special, &idx->w_rng, &idx->w_rlims};
     for (DevBuf* b : bufs) b->release();
+    range_release(idx);
     {   // the last index of the process on this device takes the shared workspaces with it
         DevPool& pl = pool_of(idx->device);
         std::lock_guard<std::mutex> g(pl.mu);
@@ -268,6 +283,7 @@ int trx_index_reset(trx_index* idx) {
     idx->n = 0; idx->cap = 0; idx->mode = MODE_EMPTY; idx->Kp = 0;
     idx->maxabs = 0.f; idx->maxnorm2 = 0.f; idx->maxerr2 = 0.f; idx->nonint = false;
     idx->n_special = 0; idx->special_overflow = false;
+    range_release(idx);
     return TRX_OK;
 }
 
@@ -440,6 +456,61 @@ static int device_cus(trx_index* idx) {
     return idx->cus;
 }
 
+// The operand copies of the integer forms of the scan (int8 copy of the corpus and of the queries; fp4 ones for bit vectors),
+// made when the index allows the form; which one runs is decided on the device (w_cls[1]).  Shared by the search and the range
+// search.  -> *try8 / *try4: whether the int8 / fp4 launches are to be enqueued (gated).
+static int prepare_int_forms(trx_index* idx, DevPool& pl, const void* q, int is_bf, int64_t nq, int64_t q_pad, int q_split, bool* try8_out,
+                             bool* try4_out, hipStream_t st) {
+    const int d = idx->d, Kp = idx->Kp;
+    int rc;
+    const bool try8 = idx->mode == MODE_PLAIN && !idx->nonint && idx->maxabs <= 127.f && d >= 256 && !q_split && !getenv("TRX_NO_I8");
+    if (try8) {
+        const int Kp8 = (int)round_up64(std::max(d, 512), 256);
+        const int64_t rows8 = idx->cap + TILE_M;
+        if (idx->c8_cap != rows8 || idx->Kp8 != Kp8) {
+            if (idx->C8) (void)hipFree(idx->C8);
+            if (idx->cbias8) (void)hipFree(idx->cbias8);
+            idx->C8 = nullptr; idx->cbias8 = nullptr; idx->c8_cap = 0; idx->c8_rows = -1;
+            HIPCHK(hipMalloc((void**)&idx->C8, (size_t)rows8 * Kp8));
+            HIPCHK(hipMalloc((void**)&idx->cbias8, (size_t)rows8 * sizeof(int)));
+            idx->c8_cap = rows8; idx->Kp8 = Kp8;
+        }
+        if (idx->c8_rows != idx->n) {
+            HIPCHK(hipMemsetAsync(idx->C8, 0, (size_t)rows8 * Kp8, st));
+            HIPCHK(launch_build_operand_i8(idx->Cg, 1, idx->n, d, Kp, idx->C8, Kp8, 1.f, st));
+            HIPCHK(launch_fill_bias_i32(idx->cnorm2, idx->n, rows8, idx->cbias8, st));
+            idx->c8_rows = idx->n;
+        }
+        if ((rc = pl.qg8.reserve((size_t)q_pad * Kp8))) return rc;
+        HIPCHK(hipMemsetAsync(pl.qg8.p, 0, (size_t)q_pad * Kp8, st));
+        HIPCHK(launch_build_operand_i8(q, is_bf, nq, d, d, (signed char*)pl.qg8.p, Kp8, idx->metric == TRX_METRIC_L2 ? 2.f : 1.f, st));
+        idx->pend.tried_i8 = 1;
+    }
+    // ... and a corpus of bit vectors (every value one of 0, +-1, +-2, +-3, +-4, +-6) an fp4 form: a third launch of each pair,
+    // run when the queries are of that kind too (w_cls[1] == 2)
+    const bool try4 = try8 && !idx->nonfp4 && !getenv("TRX_NO_FP4");
+    if (try4) {
+        const int Kp4 = (int)round_up64(std::max(d, 1024), 512) / 2;      // bytes per row: a K-step is 128 of them = 256 components, at least 4, an even number
+        const int64_t rows4 = idx->cap + TILE_M;
+        if (idx->c4_cap != rows4 || idx->Kp4 != Kp4) {
+            if (idx->C4) (void)hipFree(idx->C4);
+            idx->C4 = nullptr; idx->c4_cap = 0; idx->c4_rows = -1;
+            HIPCHK(hipMalloc((void**)&idx->C4, (size_t)rows4 * Kp4));
+            idx->c4_cap = rows4; idx->Kp4 = Kp4;
+        }
+        if (idx->c4_rows != idx->n) {
+            HIPCHK(hipMemsetAsync(idx->C4, 0, (size_t)rows4 * Kp4, st));
+            HIPCHK(launch_build_operand_fp4(idx->Cg, 1, idx->n, d, Kp, idx->C4, Kp4, st));
+            idx->c4_rows = idx->n;
+        }
+        if ((rc = pl.qg4.reserve((size_t)q_pad * Kp4))) return rc;
+        HIPCHK(hipMemsetAsync(pl.qg4.p, 0, (size_t)q_pad * Kp4, st));
+        HIPCHK(launch_build_operand_fp4(q, is_bf, nq, d, d, (unsigned char*)pl.qg4.p, Kp4, st));
+    }
+    *try8_out = try8; *try4_out = try4;
+    return TRX_OK;
+}
+
 static int search_batch(trx_index* idx, const void* q, const float* qnorm2, const float* qerr2, int64_t nq, int is_bf, int q_split, int batch_no,
                         float eps_rel, int k, float* D, int64_t* I, double* S64, hipStream_t st) {
     const int d = idx->d, Kp = idx->Kp;
@@ -523,51 +594,9 @@ static int search_batch(trx_index* idx, const void* q, const float* qnorm2, cons
     // whether the queries qualify is known on the device only (w_cls[1], classify_kernel), so both launches are enqueued
     // and gated there: exactly one of them runs, the other returns at once.  Thresholds (bootstrap, g_thr), lists and
     // everything downstream are the same keys in both forms.
-    const bool try8 = idx->mode == MODE_PLAIN && !idx->nonint && idx->maxabs <= 127.f && d >= 256 && !q_split && !getenv("TRX_NO_I8");
-    if (try8) {
-        const int Kp8 = (int)round_up64(std::max(d, 512), 256);
-        const int64_t rows8 = idx->cap + TILE_M;
-        if (idx->c8_cap != rows8 || idx->Kp8 != Kp8) {
-            if (idx->C8) (void)hipFree(idx->C8);
-            if (idx->cbias8) (void)hipFree(idx->cbias8);
-            idx->C8 = nullptr; idx->cbias8 = nullptr; idx->c8_cap = 0; idx->c8_rows = -1;
-            HIPCHK(hipMalloc((void**)&idx->C8, (size_t)rows8 * Kp8));
-            HIPCHK(hipMalloc((void**)&idx->cbias8, (size_t)rows8 * sizeof(int)));
-            idx->c8_cap = rows8; idx->Kp8 = Kp8;
-        }
-        if (idx->c8_rows != idx->n) {
-            HIPCHK(hipMemsetAsync(idx->C8, 0, (size_t)rows8 * Kp8, st));
-            HIPCHK(launch_build_operand_i8(idx->Cg, 1, idx->n, d, Kp, idx->C8, Kp8, 1.f, st));
-            HIPCHK(launch_fill_bias_i32(idx->cnorm2, idx->n, rows8, idx->cbias8, st));
-            idx->c8_rows = idx->n;
-        }
-        if ((rc = pl.qg8.reserve((size_t)q_pad * Kp8))) return rc;
-        HIPCHK(hipMemsetAsync(pl.qg8.p, 0, (size_t)q_pad * Kp8, st));
-        HIPCHK(launch_build_operand_i8(q, is_bf, nq, d, d, (signed char*)pl.qg8.p, Kp8, idx->metric == TRX_METRIC_L2 ? 2.f : 1.f, st));
-        sp.gate = (const int*)idx->w_cls.p + 1; sp.gate_want = 0;
-        idx->pend.tried_i8 = 1;
-    }
-    // ... and a corpus of bit vectors (every value one of 0, +-1, +-2, +-3, +-4, +-6) an fp4 form: a third launch of each pair,
-    // run when the queries are of that kind too (w_cls[1] == 2)
-    const bool try4 = try8 && !idx->nonfp4 && !getenv("TRX_NO_FP4");
-    if (try4) {
-        const int Kp4 = (int)round_up64(std::max(d, 1024), 512) / 2;      // bytes per row: a K-step is 128 of them = 256 components, at least 4, an even number
-        const int64_t rows4 = idx->cap + TILE_M;
-        if (idx->c4_cap != rows4 || idx->Kp4 != Kp4) {
-            if (idx->C4) (void)hipFree(idx->C4);
-            idx->C4 = nullptr; idx->c4_cap = 0; idx->c4_rows = -1;
-            HIPCHK(hipMalloc((void**)&idx->C4, (size_t)rows4 * Kp4));
-            idx->c4_cap = rows4; idx->Kp4 = Kp4;
-        }
-        if (idx->c4_rows != idx->n) {
-            HIPCHK(hipMemsetAsync(idx->C4, 0, (size_t)rows4 * Kp4, st));
-            HIPCHK(launch_build_operand_fp4(idx->Cg, 1, idx->n, d, Kp, idx->C4, Kp4, st));
-            idx->c4_rows = idx->n;
-        }
-        if ((rc = pl.qg4.reserve((size_t)q_pad * Kp4))) return rc;
-        HIPCHK(hipMemsetAsync(pl.qg4.p, 0, (size_t)q_pad * Kp4, st));
-        HIPCHK(launch_build_operand_fp4(q, is_bf, nq, d, d, (unsigned char*)pl.qg4.p, Kp4, st));
-    }
+    bool try8 = false, try4 = false;
+    if ((rc = prepare_int_forms(idx, pl, q, is_bf, nq, q_pad, q_split, &try8, &try4, st))) return rc;
+    if (try8) { sp.gate = (const int*)idx->w_cls.p + 1; sp.gate_want = 0; }
     // seed the shared thresholds: every query tile scans a few tiles (selection bookkeeping only, no lists)
     const bool boot = !getenv("TRX_NO_BOOT") && ntiles > 2;
     if (boot) {
@@ -1088,5 +1117,286 @@ int trx_faiss_tie_order_device(int64_t nq, int k2, int k, const double* S2, cons
     HIPCHK(launch_faiss_ties(nq, k2, k, S2, I2, D, I, nullptr, (hipStream_t)stream));
     return TRX_OK;
 }
+
+// ---- range search (include/trx_knn.h: trx_index_range_search) ----------------------------------------
+
+constexpr int64_t RANGE_QB = 65536;      // queries per block, as the search's batches
+
+// One block of at most RANGE_QB queries: seeds, the fixed-threshold scan, the re-score, the exact path of the queries whose lists
+// overflowed, lims, and the CSR rows, appended to the index's answer.  Synchronises the stream twice: the size of the exact path and
+// of the answer decide allocations.  The caller holds the pool's mutex.
+static int range_batch(trx_index* idx, DevPool& pl, const void* q, const float* qnorm2, const float* qerr2, int64_t nq, int is_bf, float eps_rel,
+                       float eps_round, float radius, int64_t* lims, hipStream_t st) {
+    const int d = idx->d, Kp = idx->Kp;
+    const int64_t q_pad = round_up64(nq, TILE_N);
+    const int nqt = (int)(q_pad / TILE_N);
+    const int ntiles = (int)(round_up64(idx->n, TILE_M) / TILE_M);
+    const bool f32c = keeps_f32(idx->mode);
+    const void* corig = f32c ? (const void*)idx->Co : (const void*)idx->Cg;
+    const int64_t ldc = f32c ? d : Kp;
+    const int cbf = f32c ? 0 : 1;
+    int rc;
+    // workspace: counts [RANGE_QB], exact-path marks [RANGE_QB], the exact-path list [RANGE_QB], its length, seeds [RANGE_QB]
+    if ((rc = idx->w_rng.reserve((size_t)(4 * RANGE_QB + 64) * sizeof(int)))) return rc;
+    int* cnt = (int*)idx->w_rng.p; int* exact = cnt + RANGE_QB; int* xlist = exact + RANGE_QB; int* nx = xlist + RANGE_QB;
+    float* seed = (float*)(nx + 64);
+    // more hostile rows than the index folds in (knn_common.h): every query takes the exact path, as in a search
+    const bool all_exact = idx->special_overflow;
+    int region = 0;
+    std::vector<int> ident;
+    if (!all_exact) {
+        // at most RANGE_MAX_SPLITS corpus splits: a query's lists then hold at most 4,064 rows, which the re-score sorts in LDS
+        const bool may8 = idx->mode == MODE_PLAIN && !idx->nonint && idx->maxabs <= 127.f && d >= 256 && !getenv("TRX_NO_I8");
+        const bool may4 = may8 && !idx->nonfp4 && !getenv("TRX_NO_FP4");
+        int nsplits = choose_splits(nqt, ntiles, Kp, device_cus(idx), may4 ? 0.25 : may8 ? 0.5 : 1.0, RANGE_MAX_SPLITS);
+        const int tps = (ntiles + nsplits - 1) / nsplits;
+        nsplits = (ntiles + tps - 1) / tps;
+        const int nlists = nsplits * LISTS_PER_SPLIT, cap = 127, cap_alloc = cap + 1;
+        region = nlists * cap_alloc;
+        const bool direct = is_bf && Kp == d && q_pad == nq && (((uintptr_t)q) & 15) == 0;
+        if (!direct && (rc = pl.qg.reserve((size_t)q_pad * Kp * sizeof(bf16_t)))) return rc;
+        if ((rc = pl.cand.reserve((size_t)q_pad * nlists * cap_alloc * sizeof(u64)))) return rc;
+        if ((rc = pl.cnt.reserve((size_t)q_pad * nlists * sizeof(u32)))) return rc;
+        if ((rc = pl.thr.reserve((size_t)q_pad * nlists * sizeof(u64)))) return rc;
+        if ((rc = pl.gthr.reserve((size_t)q_pad * 4 * sizeof(u32)))) return rc;
+        if (!direct) {
+            HIPCHK(hipMemsetAsync(pl.qg.p, 0, (size_t)q_pad * Kp * sizeof(bf16_t), st));
+            HIPCHK(launch_build_operand(q, is_bf, 0, nq, d, d, (bf16_t*)pl.qg.p, Kp, st));
+        }
+        ScanParams sp{};
+        sp.corpus = idx->Cg; sp.queries = direct ? (const bf16_t*)q : (const bf16_t*)pl.qg.p; sp.cbias = idx->cbias;
+        sp.Kp = Kp; sp.n_valid = (int)idx->n; sp.ntiles = ntiles; sp.tiles_per_split = tps; sp.nsplits = nsplits;
+        sp.nqtiles = nqt; sp.nq_valid = (int)nq; sp.kprime = 16; sp.cap = cap; sp.cap_alloc = cap_alloc;
+        sp.cand = (u64*)pl.cand.p; sp.cand_cnt = (u32*)pl.cnt.p; sp.cand_thr = (u64*)pl.thr.p;
+        sp.g_thr = (u32*)pl.gthr.p; sp.fixed_thr = 1;      // every threshold stays at its seed: every row that reaches it is listed
+        bool try8 = false, try4 = false;
+        if ((rc = prepare_int_forms(idx, pl, q, is_bf, nq, q_pad, 0, &try8, &try4, st))) return rc;
+        if (try8) { sp.gate = (const int*)idx->w_cls.p + 1; sp.gate_want = 0; }
+        HIPCHK(hipMemsetAsync(sp.g_thr, 0, (size_t)q_pad * 4 * sizeof(u32), st));
+        HIPCHK(launch_range_seeds(idx->metric, q, is_bf, nq, d, (double)radius, qnorm2, eps_rel, eps_round, idx->maxnorm2, qerr2, idx->maxerr2,
+                                  seed, sp.g_thr, st));
+        if (idx->timing) HIPCHK(hipEventRecord(idx->ev[0], st));
+        HIPCHK(launch_scan(sp, idx->metric, st));
+        if (try8) {      // the integer forms, gated on the device exactly as in a search (same keys, same lists)
+            ScanParams s8 = sp;
+            s8.i8 = 1; s8.gate_want = 1;
+            s8.corpus = (const bf16_t*)idx->C8; s8.queries = (const bf16_t*)pl.qg8.p; s8.cbias = (const float*)idx->cbias8; s8.Kp = idx->Kp8 / 2;
+            HIPCHK(launch_scan(s8, idx->metric, st));
+        }
+        if (try4) {
+            ScanParams s4 = sp;
+            s4.i8 = 2; s4.gate_want = 2;
+            s4.corpus = (const bf16_t*)idx->C4; s4.queries = (const bf16_t*)pl.qg4.p; s4.Kp = idx->Kp4 / 2;
+            HIPCHK(launch_scan(s4, idx->metric, st));
+        }
+        if (idx->timing) HIPCHK(hipEventRecord(idx->ev[1], st));
+        HIPCHK(hipMemsetAsync(nx, 0, sizeof(int), st));
+        RangeParams rp{};
+        rp.cand = sp.cand; rp.cand_cnt = sp.cand_cnt; rp.cand_thr = sp.cand_thr; rp.rows = sp.cand; rp.nlists = nlists; rp.cap_alloc = cap_alloc;
+        rp.corpus_orig = corig; rp.ld_c = ldc; rp.corpus_is_bf16 = cbf; rp.query_orig = q; rp.ld_q = d; rp.query_is_bf16 = is_bf;
+        rp.d = d; rp.metric = idx->metric; rp.nq = (int)nq; rp.n = idx->n; rp.radius = radius; rp.qnorm2 = qnorm2; rp.seed = seed;
+        rp.special = (const int*)idx->w_special.p; rp.nspecial = idx->n_special;
+        rp.cnt = cnt; rp.exact = exact; rp.xlist = xlist; rp.nx = nx;
+        HIPCHK(launch_range_rescore(rp, st));
+        idx->rstats.scan_launches += 1;
+        idx->rstats.n_splits = nsplits;
+    } else {
+        ident.resize((size_t)nq);
+        for (int64_t i = 0; i < nq; ++i) ident[(size_t)i] = (int)i;
+        HIPCHK(hipMemcpyAsync(xlist, ident.data(), (size_t)nq * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    int hx = (int)nq;
+    if (!all_exact) HIPCHK(hipMemcpyAsync(&hx, nx, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (idx->timing && !all_exact) {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, idx->ev[0], idx->ev[1]));
+        idx->rstats.scan_ms += ms;
+    }
+    // the exact path: every score of the query's row, counted now and written once lims is known (scored again when the queries
+    // do not fit one pass of the score buffer)
+    const int64_t per = std::max<int64_t>(1, ((int64_t)1 << 29) / std::max<int64_t>(1, idx->n * 8));
+    const int64_t chunk = std::min<int64_t>(per, std::max(hx, 1));
+    double* sc = nullptr;
+    if (hx > 0) {
+        if ((rc = idx->w_exact.reserve((size_t)chunk * idx->n * sizeof(double)))) return rc;
+        sc = (double*)idx->w_exact.p;
+        for (int64_t f0 = 0; f0 < hx; f0 += chunk) {
+            const int m = (int)std::min<int64_t>(chunk, hx - f0);
+            HIPCHK(launch_exact_scores(idx->metric, cbf, is_bf, xlist + f0, m, nullptr, idx->n, corig, ldc, q, d, d, sc, st));
+            HIPCHK(launch_range_count(idx->metric, xlist + f0, m, idx->n, sc, radius, cnt, st));
+        }
+    }
+    const int64_t base = idx->rng_total;
+    HIPCHK(launch_range_lims(cnt, (int)nq, base, lims, st));
+    int64_t total = base;
+    HIPCHK(hipMemcpyAsync(&total, lims + nq, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const int64_t bt = total - base;
+    if (bt > 0) {
+        trx_index::RangeChunk c{nullptr, nullptr, bt};
+        HIPCHK(hipMalloc((void**)&c.D, (size_t)bt * sizeof(float)));
+        hipError_t e = hipMalloc((void**)&c.I, (size_t)bt * sizeof(int64_t));
+        if (e != hipSuccess) { (void)hipFree(c.D); HIPCHK(e); }
+        idx->rng_chunks.push_back(c);
+        if (!all_exact) HIPCHK(launch_range_emit((const u64*)pl.cand.p, region, cnt, exact, lims, base, (int)nq, c.D, c.I, st));
+        for (int64_t f0 = 0; f0 < hx; f0 += chunk) {
+            const int m = (int)std::min<int64_t>(chunk, hx - f0);
+            if (hx > chunk) HIPCHK(launch_exact_scores(idx->metric, cbf, is_bf, xlist + f0, m, nullptr, idx->n, corig, ldc, q, d, d, sc, st));
+            HIPCHK(launch_range_emit_exact(idx->metric, xlist + f0, m, idx->n, sc, radius, lims, base, c.D, c.I, st));
+        }
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    idx->rng_total = total;
+    idx->rstats.n_exact += hx;
+    return TRX_OK;
+}
+
+// q, lims in device memory; the caller has checked the arguments, set the device and released the previous answer; n > 0, nq > 0
+static int range_device_core(trx_index* idx, const void* q, int64_t nq, int is_bf, float radius, int64_t* lims, hipStream_t st) {
+    const int d = idx->d;
+    int rc;
+    if (idx->mode == MODE_SPLIT) return fail(TRX_EINVAL, "range_search does not run on the three-term split form (lab build)");
+    if (idx->timing) HIPCHK(hipEventRecord(idx->ev[2], st));
+    // the query statistics of a search: class flags, fp32 |x|^2 and |x - bf16(x)|^2 of every query (the error bound's inputs)
+    if ((rc = idx->w_stats.reserve(sizeof(HostStats)))) return rc;
+    HIPCHK(hipMemsetAsync(idx->w_stats.p, 0, sizeof(HostStats), st));
+    const int64_t nq_pad = round_up64(nq, TILE_N);
+    if ((rc = idx->w_qnorm2.reserve((size_t)2 * nq_pad * sizeof(float)))) return rc;
+    float* qnorm2 = (float*)idx->w_qnorm2.p;
+    float* qerr2 = getenv("TRX_ROUND_BOUND_APRIORI") ? nullptr : qnorm2 + nq_pad;
+    HIPCHK(launch_row_stats(q, is_bf, nq, d, d, idx->w_stats.p, qnorm2, qerr2, st));
+    if ((rc = idx->w_cls.reserve(4 * sizeof(int)))) return rc;
+    HIPCHK(launch_classify(idx->w_stats.p, 0, idx->nonint ? 1 : 0, idx->maxabs, idx->Kp, d, idx->metric == TRX_METRIC_L2 ? 1 : 0,
+                           (idx->nonfp4 || getenv("TRX_NO_FP4")) ? 1 : 0, (int*)idx->w_cls.p, st));
+    // the key error bound of a search (search_device_core): fp32 queries are taken as rounded to bf16 whatever their values (no
+    // read-back): the measured rounding term is zero for those that are not
+    const float eps_rel = (float)((idx->Kp + 64) * std::ldexp(1.0, -23));
+    const bool approx = idx->mode == MODE_APPROX || !is_bf;
+    const float eps_round = approx ? (float)(std::ldexp(1.0, -7) * (1.0 + std::ldexp(1.0, -8))) : 0.f;
+    const size_t esz = is_bf ? 2 : 4;
+    bool tried8 = false;
+    {
+        DevPool& pl = pool_of(idx->device);
+        std::lock_guard<std::mutex> pool_guard(pl.mu);
+        if (pl.last) HIPCHK(hipStreamWaitEvent(st, pl.last, 0));
+        else HIPCHK(hipEventCreateWithFlags(&pl.last, hipEventDisableTiming));
+        idx->pend.tried_i8 = 0;
+        for (int64_t q0 = 0; q0 < nq; q0 += RANGE_QB) {
+            const int64_t m = std::min(RANGE_QB, nq - q0);
+            rc = range_batch(idx, pl, (const char*)q + (size_t)q0 * d * esz, qnorm2 + q0, qerr2 ? qerr2 + q0 : nullptr, m, is_bf, eps_rel, eps_round,
+                             radius, lims + q0, st);
+            if (rc) return rc;
+        }
+        tried8 = idx->pend.tried_i8 != 0;
+        idx->pend.tried_i8 = 0;
+        HIPCHK(hipEventRecord(pl.last, st));
+    }
+    int cls[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(cls, idx->w_cls.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (idx->timing) HIPCHK(hipEventRecord(idx->ev[3], st));
+    HIPCHK(hipStreamSynchronize(st));
+    idx->rstats.int8_scan = tried8 ? cls[1] : 0;
+    if (idx->timing) {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, idx->ev[2], idx->ev[3]));
+        idx->rstats.total_ms += ms;
+    }
+    return TRX_OK;
+}
+
+// argument errors first, so that they are reported without a device (tests/test_range_cpu.py)
+static int range_args(const trx_index* idx, const void* q, int64_t nq, float radius, const int64_t* lims) {
+    if (!lims) return fail(TRX_EINVAL, "lims is null");
+    if (nq < 0) return fail(TRX_EINVAL, "nq must be >= 0");
+    if (nq > 0 && !q) return fail(TRX_EINVAL, "null query pointer");
+    if (std::isnan(radius)) return fail(TRX_EINVAL, "radius is NaN (no row satisfies it)");
+    if (!idx) return fail(TRX_EINVAL, "index is null");
+    return TRX_OK;
+}
+
+// the start of a range search: the previous answer goes, the counters start from zero
+static int range_begin(trx_index* idx, int64_t nq) {
+    int rc = set_device(idx); if (rc) return rc;
+    if (idx->pend.active) { rc = finish_impl(idx); if (rc) return rc; }      // a search begun and never finished
+    range_release(idx);
+    idx->rstats = trx_range_stats{};
+    idx->rstats.nq = nq;
+    return TRX_OK;
+}
+
+int trx_index_range_search_device(trx_index* idx, const void* q, int64_t nq, int dtype, float radius, int64_t* lims, void* stream) {
+    int rc = range_args(idx, q, nq, radius, lims); if (rc) return rc;
+    if (dtype != TRX_DTYPE_F32 && dtype != TRX_DTYPE_BF16) return fail(TRX_EINVAL, "unknown dtype");
+    if ((rc = range_begin(idx, nq))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (nq == 0 || idx->n == 0) {
+        HIPCHK(hipMemsetAsync(lims, 0, (size_t)(nq + 1) * sizeof(int64_t), st));
+        HIPCHK(hipStreamSynchronize(st));
+        return TRX_OK;
+    }
+    if ((rc = range_device_core(idx, q, nq, dtype == TRX_DTYPE_BF16, radius, lims, st))) return rc;
+    idx->rstats.n_results = idx->rng_total;
+    return TRX_OK;
+}
+
+int trx_index_range_search(trx_index* idx, const void* q, int64_t nq, int dtype, float radius, int64_t* lims) {
+    int rc = range_args(idx, q, nq, radius, lims); if (rc) return rc;
+    const size_t esz = (size_t)host_dtype_size(dtype);
+    if (!esz) return fail(TRX_EINVAL, "unknown dtype");
+    if ((rc = range_begin(idx, nq))) return rc;
+    if (nq == 0 || idx->n == 0) { std::fill(lims, lims + nq + 1, (int64_t)0); return TRX_OK; }
+    // host rows in blocks of 65,536, staged as a search stages them (knn_host.h: integers narrowed to int8 where they fit), each
+    // block range-searched on the device and its lims written behind the previous block's
+    if (!idx->copy_stream) HIPCHK(hipStreamCreateWithFlags(&idx->copy_stream, hipStreamNonBlocking));
+    if ((rc = idx->w_rlims.reserve((size_t)(nq + 1) * sizeof(int64_t)))) return rc;
+    int64_t* lims_dev = (int64_t*)idx->w_rlims.p;
+    int prefer = STAGED_I8;
+    for (int64_t q0 = 0; q0 < nq; q0 += RANGE_QB) {
+        const int64_t m = std::min(RANGE_QB, nq - q0);
+        if ((rc = idx->w_stage[0].reserve(stage_capacity(m, idx->d, dtype)))) return rc;
+        int form = prefer;
+        HIPCHK(stage_host_rows((const char*)q + (size_t)q0 * idx->d * esz, dtype, m, idx->d, idx->w_stage[0].p, &form, idx->copy_stream));
+        if (form == STAGED_F32) prefer = STAGED_F32;
+        const void* qd = idx->w_stage[0].p;
+        if (form == STAGED_I8) {
+            if ((rc = idx->w_wide.reserve(staged_bytes(m, idx->d, STAGED_BF16)))) return rc;
+            HIPCHK(launch_widen_i8((const signed char*)qd, m, idx->d, (bf16_t*)idx->w_wide.p, nullptr));
+            qd = idx->w_wide.p;
+        }
+        if ((rc = range_device_core(idx, qd, m, form != STAGED_F32, radius, lims_dev + q0, nullptr))) return rc;
+    }
+    HIPCHK(hipMemcpy(lims, lims_dev, (size_t)(nq + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    idx->rstats.n_results = idx->rng_total;
+    return TRX_OK;
+}
+
+static int range_fetch(trx_index* idx, float* D, int64_t* I, hipMemcpyKind kind, hipStream_t st) {
+    if (!idx) return fail(TRX_EINVAL, "index is null");
+    if (idx->rng_total > 0 && (!D || !I)) return fail(TRX_EINVAL, "null result pointer");
+    int rc = set_device(idx); if (rc) return rc;
+    int64_t off = 0;
+    for (const auto& c : idx->rng_chunks) {
+        HIPCHK(hipMemcpyAsync(D + off, c.D, (size_t)c.count * sizeof(float), kind, st));
+        HIPCHK(hipMemcpyAsync(I + off, c.I, (size_t)c.count * sizeof(int64_t), kind, st));
+        off += c.count;
+    }
+    if (kind == hipMemcpyDeviceToHost) HIPCHK(hipStreamSynchronize(st));
+    return TRX_OK;
+}
+
+int trx_index_range_fetch(trx_index* idx, float* D, int64_t* I) { return range_fetch(idx, D, I, hipMemcpyDeviceToHost, nullptr); }
+
+int trx_index_range_fetch_device(trx_index* idx, float* D, int64_t* I, void* stream) {
+    return range_fetch(idx, D, I, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+}
+
+int trx_index_last_range_stats(const trx_index* idx, trx_range_stats* out) {
+    if (!idx || !out) return fail(TRX_EINVAL, "null argument");
+    *out = idx->rstats;
+    return TRX_OK;
+}
+
+int trx_range_stats_size(void) { return (int)sizeof(trx_range_stats); }
 
 }  // extern "C"

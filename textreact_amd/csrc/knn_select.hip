@@ -11,70 +11,13 @@
 // retrieve/retrieve_faiss.py:71, and gives the (D, I) it returns.
 #include "../../include/trx_knn.h"
 #include "knn_common.h"
+#include "knn_score.h"
 #include <float.h>
 #include <algorithm>
 #include <cstdlib>
 #include <cstdint>
 
 namespace trx {
-
-template <bool BF>
-__device__ __forceinline__ double load_as_double(const void* base, int64_t off) {
-    if (BF) return (double)bf16_to_f32(reinterpret_cast<const bf16_t*>(base)[off]);
-    return (double)reinterpret_cast<const float*>(base)[off];
-}
-
-// canonical score of (query row q, corpus row c); one thread walks the whole row in k order.
-template <bool L2, bool CBF, bool QBF>
-__device__ __forceinline__ double canonical_score(const void* qrow, const void* crow, int d) {
-    double s = 0.0;
-    // 8 components per step: 16-byte loads for bf16 rows, 2 x 16 bytes for f32 rows -- when both rows start on a dword: a
-    // multi-dword load needs that much, and bf16 rows of an odd d start on odd halfwords every other row (device bf16 queries; since
-    // round 6 also every integer host array, which reaches the device as int8 and is widened to bf16 rows of d components: the fuzzer
-    // found d = 65).  Otherwise component by component: the same chain in the same order, the same bits.
-    int k = 0;
-    const bool dword_rows = ((reinterpret_cast<uintptr_t>(qrow) | reinterpret_cast<uintptr_t>(crow)) & 3u) == 0;
-    for (; dword_rows && k + 8 <= d; k += 8) {
-        double x[8], y[8];
-        if (QBF) {
-            uint4 u = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(qrow) + k);
-            const u32 w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                x[2 * i] = (double)__uint_as_float(w[i] << 16);
-                x[2 * i + 1] = (double)__uint_as_float(w[i] & 0xffff0000u);
-            }
-        } else {
-            const float4 a = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(qrow) + k);
-            const float4 b = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(qrow) + k + 4);
-            x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
-        }
-        if (CBF) {
-            uint4 u = *reinterpret_cast<const uint4*>(reinterpret_cast<const bf16_t*>(crow) + k);
-            const u32 w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                y[2 * i] = (double)__uint_as_float(w[i] << 16);
-                y[2 * i + 1] = (double)__uint_as_float(w[i] & 0xffff0000u);
-            }
-        } else {
-            const float4 a = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(crow) + k);
-            const float4 b = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(crow) + k + 4);
-            y[0] = a.x; y[1] = a.y; y[2] = a.z; y[3] = a.w; y[4] = b.x; y[5] = b.y; y[6] = b.z; y[7] = b.w;
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            if (L2) { const double t = x[i] - y[i]; s = __builtin_fma(t, t, s); }
-            else s = __builtin_fma(x[i], y[i], s);
-        }
-    }
-    for (; k < d; ++k) {
-        const double x = load_as_double<QBF>(qrow, k), y = load_as_double<CBF>(crow, k);
-        if (L2) { const double t = x - y; s = __builtin_fma(t, t, s); }
-        else s = __builtin_fma(x, y, s);
-    }
-    return s;
-}
 
 #ifndef TRX_SEL_ABL
 #define TRX_SEL_ABL 0   // diagnostic builds: 1 = candidates are not re-scored, 2 = lists are not read (results are wrong)
@@ -1051,12 +994,11 @@ __global__ __launch_bounds__(256) void exact_pick_kernel(const int* qlist, int n
     }
 }
 
-hipError_t launch_exact_scan(int metric, int cbf, int qbf, const int* qlist, int nf, const int* nf_dev, int64_t n,
-                             const void* corpus, int64_t ld_c, const void* queries, int64_t ld_q,
-                             int d, int k, double* sc, float* D, int64_t* I, double* S64,
-                             hipStream_t st) {
-    if (nf <= 0) return hipSuccess;
-    if (n > 0) {
+// the canonical scores alone: sc[f][n] for the queries of qlist (null: f itself); also the first half of the range search's exact path
+hipError_t launch_exact_scores(int metric, int cbf, int qbf, const int* qlist, int nf, const int* nf_dev, int64_t n,
+                               const void* corpus, int64_t ld_c, const void* queries, int64_t ld_q, int d, double* sc, hipStream_t st) {
+    if (nf <= 0 || n <= 0) return hipSuccess;
+    {
         const int ce = cbf ? 2 : 4;
         // the tiled kernel needs whole 128-byte slices and 16-byte aligned rows (every index built by knn_api.hip has them
         // unless d is not a multiple of 64 / 32); the generic one takes anything
@@ -1078,7 +1020,17 @@ hipError_t launch_exact_scan(int metric, int cbf, int qbf, const int* qlist, int
             default: TRX_ES(true, true, true); break;
         }
 #undef TRX_ES
-        hipError_t e = hipGetLastError();
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_exact_scan(int metric, int cbf, int qbf, const int* qlist, int nf, const int* nf_dev, int64_t n,
+                             const void* corpus, int64_t ld_c, const void* queries, int64_t ld_q,
+                             int d, int k, double* sc, float* D, int64_t* I, double* S64,
+                             hipStream_t st) {
+    if (nf <= 0) return hipSuccess;
+    if (n > 0) {
+        hipError_t e = launch_exact_scores(metric, cbf, qbf, qlist, nf, nf_dev, n, corpus, ld_c, queries, ld_q, d, sc, st);
         if (e != hipSuccess) return e;
     }
     if (metric) hipLaunchKernelGGL(exact_pick_kernel<true>, dim3(nf), dim3(256), 0, st, qlist, nf, nf_dev, n, k, sc, D, I, S64);

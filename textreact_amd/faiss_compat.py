@@ -13,6 +13,8 @@ them to float32; the reference passes int64 / int8 fingerprints, which the libra
 its own worker threads -- same values, same results), a
 dimension mismatch raises AssertionError, ``search`` returns ``(D float32[nq,k], I int64[nq,k])``
 best first with ``I = -1`` / ``D = +-3.4e38`` padding when fewer than k vectors are indexed.
+``range_search(x, radius)`` returns ``(lims int64[nq+1], D float32[lims[-1]], I int64[lims[-1]])``: L2 rows with
+``D < radius`` (squared distance), inner-product rows with ``D > radius``, each query's rows in ascending id.
 
 Extension beyond faiss (device-resident data, used by bench.py and the sharded search): ``add`` and
 ``search`` also accept a ``torch.Tensor`` living on the index's GPU (float32 or bfloat16); search
@@ -81,6 +83,29 @@ class IndexFlat:
                                                D.ctypes.data_as(ctypes.c_void_p), I.ctypes.data_as(ctypes.c_void_p)))
         return D, I
 
+    def range_search(self, x, radius):
+        """-> (lims int64[nq + 1], D float32[lims[-1]], I int64[lims[-1]]), faiss' call shape: query i's results are
+        D[lims[i]:lims[i+1]], I[lims[i]:lims[i+1]], in ascending id.  L2: D is the squared distance and a row is returned iff
+        D < radius; inner product: iff D > radius (both strict).  D is (float) of the canonical fp64 score -- the value `search`
+        reports for the same pair -- and membership is decided on that D: the canonical rule, not faiss' fp32 sgemm, so a row whose
+        distance lies within rounding of the radius may differ from faiss (include/trx_knn.h, range search).  Host arrays of any
+        dtype `add` takes give numpy arrays; a torch tensor on the index's GPU (float32 / bfloat16) gives tensors there.
+        radius is taken as a float32; a NaN radius raises AssertionError."""
+        radius = float(radius)
+        if _is_torch(x):
+            return self._range_search_torch(x, radius)
+        x, dt = self._host_arg(x)
+        nq = x.shape[0]
+        L = _lib.lib()
+        lims = np.empty(nq + 1, dtype=np.int64)
+        _lib.check(L.trx_index_range_search(self._h, x.ctypes.data_as(ctypes.c_void_p), nq, dt, radius,
+                                            lims.ctypes.data_as(ctypes.c_void_p)))
+        total = int(lims[-1])
+        D = np.empty(total, dtype=np.float32)
+        I = np.empty(total, dtype=np.int64)
+        _lib.check(L.trx_index_range_fetch(self._h, D.ctypes.data_as(ctypes.c_void_p), I.ctypes.data_as(ctypes.c_void_p)))
+        return lims, D, I
+
     def reset(self):
         _lib.check(_lib.lib().trx_index_reset(self._h))
 
@@ -92,6 +117,13 @@ class IndexFlat:
         st = _lib.SearchStats()
         _lib.check(_lib.lib().trx_index_last_stats(self._h, ctypes.byref(st)))
         return {f: getattr(st, f) for f, _ in st._fields_}
+
+    def last_range_stats(self):
+        """counters of the most recent range_search: nq, n_results, n_exact (queries that took the exact fp64 scan), n_splits,
+        scan_launches, scan_ms / total_ms (with set_timing), int8_scan (the form the scan ran in)"""
+        st = _lib.RangeStats()
+        _lib.check(_lib.lib().trx_index_last_range_stats(self._h, ctypes.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_ if f != "reserved"}
 
     def search_s64(self, x, k):
         """torch-only: (D, I, S) with S the fp64 canonical scores (row-sharded merge input)."""
@@ -177,6 +209,21 @@ class IndexFlat:
         _lib.check(L.trx_index_search_device(self._h, ctypes.c_void_p(x.data_ptr()), nq, dt, k,
                                              ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()), st))
         return D, I
+
+    def _range_search_torch(self, x, radius):
+        import torch
+        x, dt = self._torch_arg(x)
+        nq = x.shape[0]
+        dev = torch.device("cuda", self.device)
+        lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+        st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L = _lib.lib()
+        _lib.check(L.trx_index_range_search_device(self._h, ctypes.c_void_p(x.data_ptr()), nq, dt, radius, ctypes.c_void_p(lims.data_ptr()), st))
+        total = int(lims[-1].item())
+        D = torch.empty(total, dtype=torch.float32, device=dev)
+        I = torch.empty(total, dtype=torch.int64, device=dev)
+        _lib.check(L.trx_index_range_fetch_device(self._h, ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()), st))
+        return lims, D, I
 
     def __del__(self):
         h = getattr(self, "_h", None)
